@@ -23,6 +23,11 @@ sum over replicas / max wall time over replicas.
 ONE gateway process (rank 0) takes concurrency x N streams and spreads them over the N engines
 (rank 0's in-process, ranks 1..N-1 over gRPC: parallel/replicas.py least-in-flight + prefix
 affinity); tokens/s is what that single gateway delivers.
+
+A plain run does what the headline figure needs and nothing else: set up, W warm-up waves, K timed
+waves, the result line.  --dump-outputs DIR also writes the first-token logits of the last timed
+wave's requests (DIR/first_token_logits.npy); --full adds the diagnostics on stderr; --prepare (run by the build) only writes the
+model file and fills the per-user GEMM tuning cache, so that later runs start from both.
 """
 import argparse
 import json
@@ -78,7 +83,75 @@ def parse():
                          "other ranks' engines answer it over backend.proto gRPC")
     ap.add_argument("--n-draft", type=int, default=0,
                     help="engine mode: n-gram speculative draft length (model-config n_draft); 0 = off")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed waves, write the logits each request of the last timed wave sampled "
+                         "its first token from to DIR/first_token_logits.npy: float32 [concurrency, 8192], "
+                         "row i = message i, columns = a fixed seeded sample of the vocabulary; with "
+                         "--gpus N data-parallel replica r > 0 writes DIR/first_token_logits_replica<r>.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline figure: the server-side arrival / admission view of "
+                         "every wave and the decode GEMM choices of the warm-up autotune, on stderr "
+                         "(as BENCH_ARRIVALS=1 and BENCH_DUMP_GEMM=1 do)")
+    ap.add_argument("--prepare", action="store_true",
+                    help="set up only, for the build: write the synthetic model and run the engine's warm-up, "
+                         "whose library-GEMM tuning results persist in the per-user cache "
+                         "(ops.blas_tuning_start), then exit -- later runs start from both.  A no-op without "
+                         "a GPU")
     return ap.parse_args()
+
+
+class OutputTap:
+    """--dump-outputs: keeps, for every request of the waves run inside the context, the logits
+    row its first generated token was sampled from -- what the engine hands a caller that asks for
+    it (EngineConfig.record_tokens + record_logits, switched on for these requests only: the
+    prefill step clones each request's row on the device; the decode graphs, captured without the
+    option, are not touched).  The rows stay on the device until the timed waves are over.  The
+    gateway's own callback runs unchanged afterwards, so a stream is closed only once its row is
+    kept.  Row = the message's "Request <i>:" index.
+
+    Logits, not token ids: the first step's logits depend on the prompt alone, so two runs differ
+    by the bf16 rounding of whichever GEMM kernels their prefill chunks met, while greedy token ids
+    on random-init weights turn one flipped near-tie into a different continuation."""
+
+    COLS = 8192   # a fixed, seeded sample of the vocabulary's columns
+
+    def __init__(self, eng, n):
+        self.eng, self.rows = eng, [None] * n
+
+    def __enter__(self):
+        import re
+        eng, rows = self.eng, self.rows
+        self._rec, add = (eng.cfg.record_tokens, eng.cfg.record_logits), eng.add_request
+        eng.cfg.record_tokens = eng.cfg.record_logits = True
+
+        def add_request(prompt, params, callback, *a, **k):
+            m = re.search(r"Request (\d+):", prompt) if isinstance(prompt, str) else None
+
+            def cb(ev):
+                if ev.finished and m is not None and ev.logits:
+                    rows[int(m.group(1))] = ev.logits[0]
+                return callback(ev)
+
+            return add(prompt, params, cb, *a, **k)
+
+        eng.add_request = add_request
+        return self
+
+    def __exit__(self, *exc):
+        del self.eng.add_request   # back to the class's method
+        self.eng.cfg.record_tokens, self.eng.cfg.record_logits = self._rec
+        return False
+
+    def write(self, out_dir, name):
+        import numpy as np
+        missing = [i for i, r in enumerate(self.rows) if r is None]
+        if missing:
+            raise SystemExit(f"--dump-outputs: no logits row for requests {missing[:8]}")
+        V = self.rows[0].numel()
+        cols = np.sort(np.random.default_rng(0).choice(V, size=min(V, self.COLS), replace=False))
+        out = np.stack([r.float().cpu().numpy()[cols] for r in self.rows]).astype(np.float32)
+        os.makedirs(out_dir, exist_ok=True)
+        np.save(os.path.join(out_dir, name + ".npy"), out)
 
 
 def user_messages(tok, n, plen, seed=0):
@@ -121,6 +194,13 @@ def spawn_ranks(args) -> int:
 
 def main():
     args = parse()
+    if args.prepare:
+        import torch
+        if args.gpus > 1 or "WORLD_SIZE" in os.environ:
+            raise SystemExit("--prepare is a single-process run")
+        if not torch.cuda.is_available():
+            return
+        args.mode = "engine"   # no load generators: nothing is served
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(spawn_ranks(args))
     loadgen = None
@@ -128,6 +208,8 @@ def main():
     gw = args.dp_mode == "gateway" and args.gpus > 1
     if gw and (args.mode != "http" or tp_env > 1):
         raise SystemExit("--dp-mode gateway needs --mode http and --tp 1")
+    if args.dump_outputs and (gw or args.arrival_rate > 0):
+        raise SystemExit("--dump-outputs records the synchronised waves of --dp-mode ranks")
     if args.mode == "http" and int(os.environ.get("RANK", "0")) % tp_env == 0 and \
             (not gw or int(os.environ.get("RANK", "0")) == 0):
         # client processes are started before this process touches the GPU (no fork/exec
@@ -212,7 +294,11 @@ def main():
     t0 = time.time()
     eng.warmup()
     t_capture = time.time() - t0
-    if os.environ.get("BENCH_DUMP_GEMM") and rank == 0:
+    if args.prepare:
+        print(f"bench: prepared {path} (model {t_gen:.1f} s, load {t_load:.1f} s, warm-up {t_capture:.1f} s)",
+              file=sys.stderr, flush=True)
+        return
+    if (args.full or os.environ.get("BENCH_DUMP_GEMM")) and rank == 0:
         from localai_amd import ops
         for k, v in sorted(ops._GEMM_CHOICE.items(), key=str):
             print(f"gemm choice M={k[0]} K={k[1]} ws={k[2]} -> {v}", file=sys.stderr)
@@ -235,7 +321,8 @@ def main():
     else:
         runner = EngineRunner(eng, args)
 
-    arrivals = os.environ.get("BENCH_ARRIVALS") == "1"
+    arrivals = args.full or os.environ.get("BENCH_ARRIVALS") == "1"
+    tap = OutputTap(eng, len(msgs)) if args.dump_outputs else None
 
     def wave(w):
         # the wave tag leads the message: no prompt shares more than the chat-template header with a
@@ -271,7 +358,11 @@ def main():
     for k in ("merged", "bad", "short", "split", "tail"):   # counters at the start of the timed waves
         setattr(runner, f"_{k}0", getattr(runner, k, 0))
     for s_ in range(args.steps):
-        tt, nt = wave(s_)
+        if tap is not None and s_ == args.steps - 1:
+            with tap:   # the last timed wave's outputs
+                tt, nt = wave(s_)
+        else:
+            tt, nt = wave(s_)
         ttfts += tt
         tokens += nt
     sync()
@@ -312,6 +403,8 @@ def main():
     runner.close()
     if tp > 1 and args.mode == "engine":
         eng.shutdown()   # releases the followers (HttpRunner.close already did)
+    if tap is not None:
+        tap.write(args.dump_outputs, "first_token_logits" + (f"_replica{replica}" if replica else ""))
     if rank == 0:
         value = tot_tokens / max_el
         seq = args.prompt_len + args.max_tokens

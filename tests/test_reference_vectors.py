@@ -5,7 +5,7 @@
 - pkg/functions/parse_test.go                   (24 live cases + 1 pending PIt kept as xfail)
 - core/backend/llm_test.go                      (6 Finetune cases)
 - core/config/backend_config_test.go            (Validate x3 incl. the embedded hermes-2-pro-mistral
-                                                 YAML read from the reference tree, not the network;
+                                                 YAML's settings from tests/golden, not the network;
                                                  HasUsecases matrix)
 
 The Go assertion style is kept: every non-empty expected line is a SUBSTRING of the generated
@@ -21,7 +21,9 @@ from localai_amd.config.backend_config import (FLAG_ANY, FLAG_CHAT, FLAG_COMPLET
                                                FLAG_SOUND_GENERATION, FLAG_TRANSCRIPT, FLAG_TTS, BackendConfig)
 from localai_amd.gateway.inference import finetune
 
-REF = "/root/reference"
+# the settings of the reference's embedded hermes-2-pro-mistral model config (its prompt templates
+# and usage text, which Validate never reads, are not stored)
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 
 
 def _create_function(field1, field2, name, properties):
@@ -428,10 +430,7 @@ def test_validate_rejects_relative_backend_path(tmp_path):
 def test_validate_accepts_plain_and_embedded_hermes():
     c = BackendConfig(yaml.safe_load('name: bar-baz\nbackend: "foo-bar"\nparameters:\n  model: "foo-bar"'))
     assert c.name == "bar-baz" and c.validate() is True
-    p = os.path.join(REF, "embedded", "models", "hermes-2-pro-mistral.yaml")
-    if not os.path.exists(p):
-        pytest.skip("reference tree not mounted")
-    with open(p) as f:
+    with open(os.path.join(GOLDEN, "hermes-2-pro-mistral.yaml")) as f:
         h = BackendConfig(yaml.safe_load(f))
     assert h.name == "hermes-2-pro-mistral" and h.validate() is True
 
